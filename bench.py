@@ -10,13 +10,25 @@ memory-sum ladder to its steady state, so any window of K steps carries K / P bl
 level (reported as ladder_window).  Other lines: --config C2 --ntraj 1 (the north-star 1-trajectory
 comparison), --config C5 --ntraj 32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU, RCCL reduce)
 
 Timed window per rank: barrier + device sync, the K steps, device sync (the rank's clock stops
 there), then a closing barrier; value uses the MAX of the ranks' window times.
 
-Prints one JSON line (rank 0).  roofline: the dominant kernel (far-field memory-kernel
+A plain run does what the headline needs and nothing else: setup, ladder fill, warm-up, the K timed
+steps (the window starts at step 2 x the largest ladder block + W), the ensemble reduce, and one
+JSON line (rank 0) with value, ms_per_step, the plan and the whole-step roofline (arithmetic on
+ms_per_step).  Inputs are seeded, so two plain runs with the same arguments step the same
+trajectories, and --dump-outputs DIR writes what a caller of the timed path holds after its last
+step -- momenta, positions and the last force of every trajectory, [ntraj][nph] -- as DIR/p.npy,
+DIR/q.npy, DIR/f.npy (float64; a seeded sample of an array past its share of 64 MB; rank r > 0 of a
+multi-rank run writes <name>.rank<r>.npy).
+
+--full adds everything else, each in runs of its own.  window_phase: K-step windows scanned over the
+largest level's period, the timed window placed at the phase closest to their mean (not with
+--dump-outputs: the scan picks the window by the clock, a dump wants the same window every run).
+roofline: the dominant kernel (far-field memory-kernel
 contraction, cgemm_kernel) timed by its own device timestamps (first workgroup start to last
 workgroup end of every launch, s_memrealtime) over a second window of the same K steps, HIP events
 on its stream reported beside them; chain_roofline: the per-step chain's launches timed the same
@@ -38,6 +50,8 @@ sys.path.insert(0, ROOT)
 
 FP64_MFMA_PEAK_TFLOPS = 78.6   # MI355X dense FP64 matrix (AMD spec; == FP64 vector peak)
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
+SCAN_STEPS_MAX = 1 << 19       # --full: steps the phase scan may run in all (~25 s at C3)
+DUMP_BYTES_MAX = 64 << 20      # --dump-outputs: bytes written in all
 
 
 def log(*a):
@@ -142,6 +156,20 @@ def cpu_single_pass(baths_host, dyn, nph, dt, nmd, ntraj, budget_s=8.0):
 METRIC = "GLE steps/sec/GPU, 300-atom junction, 1024-step kernel, 64-traj ensemble"
 
 
+def dump_outputs(dirname, arrays, rank=0):
+    """Write {name: array} as dirname/<name>.npy (float64), DUMP_BYTES_MAX in all: an array larger
+    than its equal share is written as a fixed sample of its flattened elements (sorted indices drawn
+    with a seed that depends on nothing but the array's size, so two builds write the same elements)."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BYTES_MAX // max(len(arrays), 1) // 8
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + (".rank%d" % rank if rank else "") + ".npy"), a)
+
+
 def loaded_runtime():
     """Paths of the HIP / HSA / RCCL runtimes mapped into this process (torch ships its own copies;
     whichever is loaded first serves every later library that needs the same soname)."""
@@ -225,8 +253,8 @@ def main():
     ap.add_argument("--fill", type=int, default=-1,
                     help="untimed steps before the warm-up that bring the memory-sum ladder to its steady "
                          "state (history older than the largest level's window); -1 = 2 x the largest "
-                         "block length, then a scan of K-step windows over the largest level's period "
-                         "and the timed window at the phase closest to the mean")
+                         "block length, and with --full a scan of K-step windows over the largest level's "
+                         "period and the timed window at the phase closest to the mean")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to "
                          "rehearse the multi-rank path, e.g. with --same-device on a one-GPU box)")
@@ -239,7 +267,12 @@ def main():
     ap.add_argument("--stream-noise", action="store_true",
                     help="generate the coloured noise through the streamed-factor path whatever the bath size "
                          "(the C5 path; rehearses the node-shared factorisation at small configs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the phase scan that places the timed window, the far-field and "
+                         "chain rooflines (a second and a third window of the same steps) and the CPU baselines")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the state after the last timed step (p, q, f of every trajectory) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--single-pass-budget", type=float, default=8.0,
                     help="seconds of the best-effort batched CPU context number (0: skip)")
@@ -344,8 +377,11 @@ def main():
     phase = None
     fill = 2 * ptop if args.fill < 0 else args.fill
     m.steps(fill)
-    nscan = ptop // math.gcd(args.steps, ptop)
-    if args.fill < 0 and levels and nscan > 1:
+    # the scan times windows of its own and picks the timed one by the clock: --full only, and not
+    # when the outputs are dumped (every run must then time the same steps); at most SCAN_STEPS_MAX
+    # steps in all, so a long window, which covers many periods anyway, is not scanned for minutes
+    nscan = min(ptop // math.gcd(args.steps, ptop), SCAN_STEPS_MAX // max(args.steps, 1))
+    if args.full and not args.dump_outputs and args.fill < 0 and levels and nscan > 1:
         # The ladder's background work within a short window depends on where the window falls in
         # the largest level's period (blocks start at multiples of P, their pieces follow), so a
         # K-step window is timed at every phase it can take (consecutive untimed windows, each
@@ -390,24 +426,28 @@ def main():
     barrier()
     log("[bench] rank %d host enqueue %.3f ms of %.3f ms timed" % (rank, t_enq * 1e3, el * 1e3))
     window_levels = st.profile_levels()
-    # roofline: HIP events around every launch of the dominant kernel over a second window of the
-    # same K steps right after the timed one (same steady state, same piece schedule phase); the
+    if args.dump_outputs:
+        # the state a caller of m.steps(K) holds after the timed window, before anything else steps
+        p_end, q_end, _ = st.get_state()
+        dump_outputs(args.dump_outputs, {"p": p_end, "q": q_end, "f": st.get_force()}, rank)
+    prof = {"launches": 0}
+    # roofline (--full): HIP events around every launch of the dominant kernel over a second window
+    # of the same K steps right after the timed one (same steady state, same piece schedule phase); the
     # events add launch-queue packets (1-6 % per step), so the headline window runs without them.
     # Fused schedule: the far-field GEMMs ride in the chain launches, which the third window times.
-    if not detail["far_fused"]:
+    if args.full and not detail["far_fused"]:
         st.profile(True, events=True)
         m.steps(args.steps)
         st.sync()
         prof = st.profile_read()
-    else:
-        prof = {"launches": 0}
-    # the chain's own per-workgroup stamps in a third window of the same K steps (apart from the
-    # far-field timing, whose launches the chain stamps would otherwise share the window with)
-    st.profile(True, events=False, chain=True)
-    m.steps(args.steps)
-    st.sync()
-    pch = st.profile_read()
-    prof.update({k: pch[k] for k in ("chain_launches", "chain_ms", "chain_flops")})
+    if args.full:
+        # the chain's own per-workgroup stamps in a third window of the same K steps (apart from the
+        # far-field timing, whose launches the chain stamps would otherwise share the window with)
+        st.profile(True, events=False, chain=True)
+        m.steps(args.steps)
+        st.sync()
+        pch = st.profile_read()
+        prof.update({k: pch[k] for k in ("chain_launches", "chain_ms", "chain_flops")})
     st.profile(False)
     # one reduce of the time-averaged current statistics (the ensemble output)
     sums = m._reduce(st.current_sums())
@@ -453,6 +493,8 @@ def main():
         "fill_steps": fill,
         "window_t0": int(t_now + fill + args.warmup),
         "window_phase": phase,
+        "full": bool(args.full),
+        "dumped_outputs": args.dump_outputs or None,
         # per ladder level: blocks issued in the timed window vs the steady-state share K / P
         "ladder_window": [{"P": P, "blocks": round(bl, 3), "steady": round(args.steps / P, 3)}
                           for P, bl in window_levels],
@@ -559,7 +601,7 @@ def main():
     res["ensemble_reduce"] = {"doubles": int(sums.size), "backend": (args.dist_backend if dist is not None else "none"),
                               "world": world}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         noise = [st.get_noise(i)[0] for i in range(len(baths))]
         bh = []
         for i, b in enumerate(baths):

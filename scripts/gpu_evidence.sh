@@ -52,9 +52,9 @@ tests)
     || fail tests $O/gpu_tests.log
   tail -2 $O/gpu_tests.log ;;
 lines)
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_c3_20x5.json 2> $O/bench_c3_20x5.err || fail b20 $O/bench_c3_20x5.err
-  timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err || fail b512 $O/bench_c3.err
-  timeout -k 10 300 python bench.py --config C2 --ntraj 1 --steps 256 --warmup 32 > $O/bench_c2.json 2> $O/bench_c2.err || fail c2 $O/bench_c2.err
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_c3_20x5.json 2> $O/bench_c3_20x5.err || fail b20 $O/bench_c3_20x5.err
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench_c3.json 2> $O/bench_c3.err || fail b512 $O/bench_c3.err
+  timeout -k 10 300 python bench.py --full --config C2 --ntraj 1 --steps 256 --warmup 32 > $O/bench_c2.json 2> $O/bench_c2.err || fail c2 $O/bench_c2.err
   summ $O/bench_c3_20x5.json $O/bench_c3.json $O/bench_c2.json ;;
 c1)
   timeout -k 10 300 python scripts/c1_driver_timing.py --nmd 1024 > $O/c1_driver_timing.json 2> $O/c1_driver_timing.err || fail c1 $O/c1_driver_timing.err
@@ -66,9 +66,9 @@ noiseshare)
 rehearse_share)
   # 8 ranks on one GPU over gloo with the C3 noise streamed: every rank's setup, noise phase and
   # factorisation count (noise.NodeShare: the counts add up to one rank's)
-  timeout -k 10 600 python bench.py --gpus 8 --same-device --dist-backend gloo --ntraj 8 --stream-noise --steps 8 --warmup 2 \
+  timeout -k 10 600 python bench.py --full --gpus 8 --same-device --dist-backend gloo --ntraj 8 --stream-noise --steps 8 --warmup 2 \
     --fill 16 --no-cpu-baseline > $O/rehearsal_share8.json 2> $O/rehearsal_share8.err || fail share8 $O/rehearsal_share8.err
-  timeout -k 10 600 python bench.py --ntraj 8 --stream-noise --steps 8 --warmup 2 --fill 16 --no-cpu-baseline \
+  timeout -k 10 600 python bench.py --full --ntraj 8 --stream-noise --steps 8 --warmup 2 --fill 16 --no-cpu-baseline \
     > $O/rehearsal_share1.json 2> $O/rehearsal_share1.err || fail share1 $O/rehearsal_share1.err
   python3 -c "import json,sys
 for f in sys.argv[1:]:
@@ -77,7 +77,7 @@ c4shape)
   # BASELINE config 4's shape (512 trajectories over 8 ranks, 64 each) rehearsed on one GPU: 8 gloo
   # ranks on device 0 (the control flow, the node-shared noise factorisation and the reduce; the
   # rate is 8 ranks time-sharing one GPU, not the 8-GPU node's)
-  timeout -k 10 900 python bench.py --gpus 8 --same-device --dist-backend gloo --ntraj 64 --steps 20 --warmup 5 \
+  timeout -k 10 900 python bench.py --full --gpus 8 --same-device --dist-backend gloo --ntraj 64 --steps 20 --warmup 5 \
     --no-cpu-baseline > $O/c4shape_8x64.json 2> $O/c4shape_8x64.err || fail c4shape $O/c4shape_8x64.err
   summ $O/c4shape_8x64.json ;;
 c5run)
@@ -87,21 +87,21 @@ negf)
   timeout -k 10 300 python -u -m pytest tests/test_gpu_negf.py -x -q -m gpu --timeout 200 --timeout-method thread > $O/negf.log 2>&1 || fail negf $O/negf.log
   tail -3 $O/negf.log ;;
 c5)
-  timeout -k 10 600 python bench.py --config C5 --ntraj 32 --steps 256 --warmup 32 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err || fail c5 $O/bench_c5.err
+  timeout -k 10 600 python bench.py --full --config C5 --ntraj 32 --steps 256 --warmup 32 --no-cpu-baseline > $O/bench_c5.json 2> $O/bench_c5.err || fail c5 $O/bench_c5.err
   summ $O/bench_c5.json ;;
 rccl)
   python3 -c "import torch; print('stream priority range (least, greatest):', torch.cuda.Stream.priority_range())"
   for r in 1 2; do
-    timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_plain20_$r.json 2> $O/rccl_plain20_$r.err || fail plain $O/rccl_plain20_$r.err
+    timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_plain20_$r.json 2> $O/rccl_plain20_$r.err || fail plain $O/rccl_plain20_$r.err
     port=$((port+1))
-    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_nccl20_$r.json 2> $O/rccl_nccl20_$r.err || fail nccl $O/rccl_nccl20_$r.err
+    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/rccl_nccl20_$r.json 2> $O/rccl_nccl20_$r.err || fail nccl $O/rccl_nccl20_$r.err
     port=$((port+1))
-    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --early-collective > $O/rccl_ncclfirst20_$r.json 2> $O/rccl_ncclfirst20_$r.err || fail ncclfirst $O/rccl_ncclfirst20_$r.err
-    timeout -k 10 300 python bench.py --no-cpu-baseline > $O/rccl_plain512_$r.json 2> $O/rccl_plain512_$r.err || fail plain512 $O/rccl_plain512_$r.err
+    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --early-collective > $O/rccl_ncclfirst20_$r.json 2> $O/rccl_ncclfirst20_$r.err || fail ncclfirst $O/rccl_ncclfirst20_$r.err
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/rccl_plain512_$r.json 2> $O/rccl_plain512_$r.err || fail plain512 $O/rccl_plain512_$r.err
     port=$((port+1))
-    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --no-cpu-baseline > $O/rccl_nccl512_$r.json 2> $O/rccl_nccl512_$r.err || fail nccl512 $O/rccl_nccl512_$r.err
+    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --no-cpu-baseline > $O/rccl_nccl512_$r.json 2> $O/rccl_nccl512_$r.err || fail nccl512 $O/rccl_nccl512_$r.err
   done
-  timeout -k 10 400 python bench.py --gpus 8 --same-device --dist-backend gloo --ntraj 8 --noise white --steps 20 --warmup 5 \
+  timeout -k 10 400 python bench.py --full --gpus 8 --same-device --dist-backend gloo --ntraj 8 --noise white --steps 20 --warmup 5 \
     --no-cpu-baseline > $O/rehearsal_gloo8.json 2> $O/rehearsal_gloo8.err || fail gloo8 $O/rehearsal_gloo8.err
   summ $O/rccl_*.json $O/rehearsal_gloo8.json ;;
 runtime)
@@ -109,12 +109,12 @@ runtime)
   # bundled copy), torchrun world-1 over gloo (torch first, no RCCL) and over nccl; interleaved twice
   for r in 1 2; do for K in 20 512; do
     W=$([ $K = 20 ] && echo 5 || echo 64)
-    timeout -k 10 300 python bench.py --steps $K --warmup $W --no-cpu-baseline > $O/rt_plain$K\_$r.json 2> $O/rt_plain$K\_$r.err || fail plain $O/rt_plain$K\_$r.err
-    timeout -k 10 300 python -c "import torch, runpy, sys; sys.argv = ['bench.py', '--steps', '$K', '--warmup', '$W', '--no-cpu-baseline']; runpy.run_path('bench.py', run_name='__main__')" > $O/rt_torchfirst$K\_$r.json 2> $O/rt_torchfirst$K\_$r.err || fail torchfirst $O/rt_torchfirst$K\_$r.err
+    timeout -k 10 300 python bench.py --full --steps $K --warmup $W --no-cpu-baseline > $O/rt_plain$K\_$r.json 2> $O/rt_plain$K\_$r.err || fail plain $O/rt_plain$K\_$r.err
+    timeout -k 10 300 python -c "import torch, runpy, sys; sys.argv = ['bench.py', '--full', '--steps', '$K', '--warmup', '$W', '--no-cpu-baseline']; runpy.run_path('bench.py', run_name='__main__')" > $O/rt_torchfirst$K\_$r.json 2> $O/rt_torchfirst$K\_$r.err || fail torchfirst $O/rt_torchfirst$K\_$r.err
     port=$((port+1))
-    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --dist-backend gloo --steps $K --warmup $W --no-cpu-baseline > $O/rt_gloo$K\_$r.json 2> $O/rt_gloo$K\_$r.err || fail gloo $O/rt_gloo$K\_$r.err
+    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --dist-backend gloo --steps $K --warmup $W --no-cpu-baseline > $O/rt_gloo$K\_$r.json 2> $O/rt_gloo$K\_$r.err || fail gloo $O/rt_gloo$K\_$r.err
     port=$((port+1))
-    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/rt_nccl$K\_$r.json 2> $O/rt_nccl$K\_$r.err || fail nccl $O/rt_nccl$K\_$r.err
+    timeout -k 10 300 $TR 1 --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus 1 --steps $K --warmup $W --no-cpu-baseline > $O/rt_nccl$K\_$r.json 2> $O/rt_nccl$K\_$r.err || fail nccl $O/rt_nccl$K\_$r.err
   done; done
   summ $O/rt_*.json
   python3 -c "
@@ -180,7 +180,7 @@ trace|trace_c5|trace_c2)
   esac
   mkdir -p $O/prof_$n
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$n -o run -- \
-    python3 bench.py $A > $O/prof_$n/bench.json 2> $O/prof_$n/bench.err || fail trace $O/prof_$n/bench.err
+    python3 bench.py --full $A > $O/prof_$n/bench.json 2> $O/prof_$n/bench.err || fail trace $O/prof_$n/bench.err
   N=$(python3 -c "import json;print(json.load(open('$O/prof_$n/bench.json'))['roofline']['launches'])")
   python3 scripts/trace_summary.py $O/prof_$n/run_kernel_trace.csv --steps --gaps --last $K $N --skip $N > $O/prof_$n/summary.txt
   tail -8 $O/prof_$n/summary.txt ;;
@@ -190,7 +190,7 @@ blocklen)
     case $c in
       c3) A="" ;; c2) A="--config C2 --ntraj 1 --steps 256 --warmup 32" ;; c5) A="--config C5 --ntraj 32 --steps 256 --warmup 32" ;;
     esac
-    timeout -k 10 400 python bench.py --no-cpu-baseline --block-len $bl $A > $O/${c}_bl${bl}_$r.json 2> $O/${c}_bl${bl}_$r.err \
+    timeout -k 10 400 python bench.py --full --no-cpu-baseline --block-len $bl $A > $O/${c}_bl${bl}_$r.json 2> $O/${c}_bl${bl}_$r.err \
       || fail "blocklen $c $bl" $O/${c}_bl${bl}_$r.err
   done; done; done
   summ $O/*_bl*_*.json ;;
@@ -199,7 +199,7 @@ pmc|pmc_c5)
   mkdir -p $O/pmc_$n
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 600 rocprofv3 --pmc $c --output-format csv -d $O/pmc_$n/$c -o run -- \
-      python3 bench.py $A > $O/pmc_$n/$c.json 2> $O/pmc_$n/$c.err || fail "pmc $c" $O/pmc_$n/$c.err
+      python3 bench.py --full $A > $O/pmc_$n/$c.json 2> $O/pmc_$n/$c.err || fail "pmc $c" $O/pmc_$n/$c.err
   done
   python3 scripts/pmc_summary.py $O/pmc_$n $O/pmc_$n/traffic_cgemm.json --kernel cgemm_kernel $cfg
   python3 scripts/pmc_summary.py $O/pmc_$n $O/pmc_$n/traffic_chain.json --kernel chain_kernel $cfg --last ${CHAIN_LAST:-512} --skip-chain-window 0 ;;

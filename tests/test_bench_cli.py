@@ -38,6 +38,29 @@ def test_spawn_command_shape():
     assert cmd[-5].endswith("bench.py") and cmd[-4:] == ["--gpus", "4", "--steps", "20"]
 
 
+def test_dump_outputs_writes_float64_within_the_byte_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float64; an array past its share of the byte
+    budget is written as the same sorted sample of its elements every time."""
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(0)
+    small = rng.normal(size=(3, 5)).astype(np.float32)
+    big = rng.normal(size=(40, 25))
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 2 * 100 * 8)   # 100 doubles per array
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float64 and a_big.dtype == np.float64
+    assert np.array_equal(a_small, small.astype(np.float64))
+    assert a_big.shape == (100,) and np.all(np.isin(a_big, big))
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 2 * 100 * 8 + 2 * 128
+    bench.dump_outputs(str(tmp_path / "r"), {"small": small}, rank=3)
+    assert os.listdir(tmp_path / "r") == ["small.rank3.npy"]
+
+
 def test_rank_env_matching_gpus_is_a_rank(monkeypatch):
     import argparse
 

@@ -108,13 +108,14 @@ def test_bench_world1_nccl_under_torchrun(tmp_path):
     joins a world-1 nccl (RCCL) process group, so RCCL's communicator and torch's stream pools exist
     beside the stepper's streams, and the window is bracketed by RCCL barriers.  The line must report
     the group and stay at the plain run's rate: the bound (70 us/step at C3, 20 steps) sits between
-    the plain line (~50 us) and the hardware-queue sharing trap of profiles/r04 (~115 us)."""
+    the plain line (~50 us) and the hardware-queue sharing trap of profiles/r04 (~115 us).  --full:
+    the 20-step window is placed by the phase scan, as when the bound was set."""
     env = _env(HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--noise", "white"]
+           "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--noise", "white"]
     res = _bench_line(subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400, cwd=str(tmp_path)))
     assert res["n_gpus"] == 1 and res["config"]["ntraj_total"] == 64
     assert res["ensemble_reduce"]["backend"] == "nccl" and res["ensemble_reduce"]["world"] == 1
