@@ -136,6 +136,40 @@ int gle_set_dyn(gle_handle* h, const double* dyn);
 /* md.AddConstr (md.py:189) flattened: the DOF indices ApplyConstraint zeroes (md.py:782-794) */
 int gle_set_constraint(gle_handle* h, const int64_t* dofs, int64_t n);
 
+/* ---- device-resident anharmonic pair force field -------------------------------------------- */
+/* A fixed list of atom pairs; each pair has a type, each type a style and four parameters (eV, A):
+ *   GLE_PAIR_HARMONIC  U = k/2 (r - r0)^2                      par = k, r0
+ *   GLE_PAIR_MORSE     U = D (1 - exp(-a (r - r0)))^2           par = D, a, r0
+ *   GLE_PAIR_LJ        U = 4 eps ((sigma/r)^12 - (sigma/r)^6)   par = eps, sigma
+ * with r = |x_j + shift_ij - x_i| and x = xyz0 + conv * q (element-wise, lammpsdriver.py:70-84).
+ * The force is exactly the sum over the listed pairs: no cutoff, no list rebuild (a junction that
+ * does not diffuse); the potential force of the stepper is conv * F(q) - f0, f0 = conv * F(0), what
+ * lammpsdriver.force returns.  While a field is set it takes the place of dyn as the potential (as a
+ * driver does in md.potforce): gle_run and gle_step_begin / gle_step_end with fpot == NULL evaluate
+ * it on the device with md.potforce's cache rule per trajectory (reuse the force while
+ * max_d |q - q0| < 1e-9 of the last evaluated point q0, md.py:449-450, 767-779) and step on the
+ * two-launch path; a composed-step plan is not used.
+ *   xyz0, conv  [3 natom]; requires nph == 3 natom
+ *   pair_i, pair_j, pair_type  [npair]; shift [npair][3] image vectors (A) or NULL for zeros
+ *   style [ntype], par [ntype][4]
+ * npair == 0 removes the field.  Setting, replacing or removing a field empties the potential-force
+ * cache: the next force call evaluates every trajectory.  GLE_ERR_ARG (nothing is uploaded, the
+ * previous field stays): nph != 3 natom, an index or type out of range, i == j with zero shift, an
+ * unknown style, a non-finite parameter or a non-positive r0 / sigma / a, coincident atoms of a pair
+ * at q = 0.  (A field that passes these checks and still has a non-finite force at q = 0, by
+ * overflow, is GLE_ERR_ARG too, and leaves no field set.) */
+#define GLE_PAIR_HARMONIC 0
+#define GLE_PAIR_MORSE 1
+#define GLE_PAIR_LJ 2
+int gle_set_pair_force(gle_handle* h, int64_t natom, const double* xyz0, const double* conv,
+                       int64_t npair, const int64_t* pair_i, const int64_t* pair_j,
+                       const int32_t* pair_type, const double* shift, int32_t ntype,
+                       const int32_t* style, const double* par);
+/* The field's force at q: q, f [ntraj][nph].  No cache, no change of the stepper's state. */
+int gle_eval_force(gle_handle* h, const double* q, double* f);
+/* count [ntraj]: cumulative evaluations of the field by the stepper per trajectory (cache misses). */
+int gle_force_evals(gle_handle* h, int64_t* count);
+
 /* ---- state ---------------------------------------------------------------------------- */
 /* md.p, md.q, md.t (md.py:372, 411).  p, q: [ntraj][nph].  Resets the potential-force cache
  * (md.q0 = [], md.py:105) and re-derives the memory sums from the current history. */
@@ -213,7 +247,8 @@ int gle_step_begin(gle_handle* h, const double* fpot, double* q_tilde_out);
 /* Phase B: the two velocity iterations at q~ (md.py:401-404) and the constraints (:407-408).
  * fpot_qt [ntraj][nph] host force at q~ or NULL for the harmonic force. */
 int gle_step_end(gle_handle* h, const double* fpot_qt);
-/* nsteps full steps with the harmonic force, entirely on the device (no host round trips). */
+/* nsteps full steps with the harmonic force, or with the pair force field when one is set
+ * (gle_set_pair_force), entirely on the device (no host round trips). */
 int gle_run(gle_handle* h, int64_t nsteps);
 int gle_sync(gle_handle* h);
 

@@ -36,7 +36,10 @@ EXPORTS = [
     "gle_comm_allreduce", "gle_noise_stream_abort", "gle_device_mem_info", "gle_noise_stream_shared",
     "gle_noise_stream_retain", "gle_noise_stream_retained", "gle_noise_stream_replay", "gle_get_full_history",
     "gle_host_alloc", "gle_host_free", "gle_cache_audit", "gle_noise_stream_retain_cap", "gle_chain_work",
+    "gle_set_pair_force", "gle_eval_force", "gle_force_evals",
 ]
+
+PAIR_HARMONIC, PAIR_MORSE, PAIR_LJ = 0, 1, 2  # hipgle.h GLE_PAIR_*
 
 REC_P, REC_Q, REC_F, REC_HIST = 1, 2, 4, 8
 
@@ -75,6 +78,11 @@ _SIGS = {
     "gle_gamt": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _D, _D, _D]),
     "gle_set_dyn": (ctypes.c_int, [_P, _D]),
     "gle_set_constraint": (ctypes.c_int, [_P, _I64, ctypes.c_int64]),
+    "gle_set_pair_force": (ctypes.c_int, [_P, ctypes.c_int64, _D, _D, ctypes.c_int64, _I64, _I64,
+                                          ctypes.POINTER(ctypes.c_int32), _D, ctypes.c_int32,
+                                          ctypes.POINTER(ctypes.c_int32), _D]),
+    "gle_eval_force": (ctypes.c_int, [_P, _D, _D]),
+    "gle_force_evals": (ctypes.c_int, [_P, _I64]),
     "gle_set_state": (ctypes.c_int, [_P, _D, _D, ctypes.c_int64]),
     "gle_get_state": (ctypes.c_int, [_P, _D, _D, _I64]),
     "gle_set_history": (ctypes.c_int, [_P, ctypes.c_int32, _D]),
@@ -345,6 +353,47 @@ class Stepper:
         d = np.ascontiguousarray(np.asarray(sorted(set(int(x) for x in dofs)), dtype=np.int64))
         self._chk(self.lib.gle_set_constraint(self.h, d.ctypes.data_as(_I64), len(d)),
                   "gle_set_constraint")
+
+    def set_pair_force(self, xyz0, conv, pair_i, pair_j, pair_type, styles, params, shift=None):
+        """Device-resident pair force field (gle_set_pair_force): xyz0, conv (3 natom,); pair_i,
+        pair_j, pair_type (npair,); styles (ntype,) of PAIR_*; params (ntype, 4); shift (npair, 3) or
+        None.  While set it is the potential of run / step_begin(None) / step_end(None)."""
+        xyz0, conv = _f64(xyz0).ravel(), _f64(conv).ravel()
+        pi = np.ascontiguousarray(np.asarray(pair_i, dtype=np.int64).ravel())
+        pj = np.ascontiguousarray(np.asarray(pair_j, dtype=np.int64).ravel())
+        pt = np.ascontiguousarray(np.asarray(pair_type, dtype=np.int32).ravel())
+        st = np.ascontiguousarray(np.asarray(styles, dtype=np.int32).ravel())
+        par = _f64(params)
+        if len(xyz0) % 3 or len(conv) != len(xyz0):
+            raise ValueError("set_pair_force: xyz0 and conv must both be (3 natom,)")
+        if not (len(pi) == len(pj) == len(pt)) or len(pi) == 0:
+            raise ValueError("set_pair_force: pair_i, pair_j, pair_type must be equally long and not empty")
+        if par.shape != (len(st), 4):
+            raise ValueError("set_pair_force: params must be (ntype, 4)")
+        sh = None if shift is None else _f64(shift, (len(pi), 3))
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        self._chk(self.lib.gle_set_pair_force(self.h, len(xyz0) // 3, _ptr(xyz0), _ptr(conv), len(pi),
+                                              pi.ctypes.data_as(_I64), pj.ctypes.data_as(_I64),
+                                              pt.ctypes.data_as(i32), _ptr(sh), len(st), st.ctypes.data_as(i32),
+                                              _ptr(par)), "gle_set_pair_force")
+
+    def clear_pair_force(self):
+        """Remove the pair force field (gle_set_pair_force with npair = 0): dyn is the potential again."""
+        self._chk(self.lib.gle_set_pair_force(self.h, 0, None, None, 0, None, None, None, None, 0, None, None),
+                  "gle_set_pair_force")
+
+    def eval_force(self, q):
+        """The field's force at q (ntraj, nph): no cache, no state change (gle_eval_force)."""
+        q = _f64(q, (self.ntraj, self.nph))
+        out = np.empty((self.ntraj, self.nph))
+        self._chk(self.lib.gle_eval_force(self.h, _ptr(q), _ptr(out)), "gle_eval_force")
+        return out
+
+    def force_evals(self):
+        """Cumulative evaluations of the field per trajectory (cache misses; gle_force_evals)."""
+        out = np.zeros(self.ntraj, dtype=np.int64)
+        self._chk(self.lib.gle_force_evals(self.h, out.ctypes.data_as(_I64)), "gle_force_evals")
+        return out
 
     def set_state(self, p, q, t):
         p = _f64(p, (self.ntraj, self.nph))

@@ -247,6 +247,19 @@ struct gle_handle {
   bool need_prime = true;
   bool pot_cache_exact = false;  // q_t == q~_{t-1} bitwise (no constraints): id0 cache hit
   bool host_force_step = false;
+  // device-resident pair force field (gle_set_pair_force): takes the place of dyn as the potential
+  // while set; its launches write Fc where a host force is uploaded, the stages run as for one.
+  // d_ff_Q0 / d_ff_flag: the field's own potential cache (the point and flag of the last evaluation)
+  bool ff_set = false;
+  int32_t ff_natom = 0;
+  int64_t ff_nnbr = 0;
+  int32_t* d_ff_rp = nullptr;
+  PairNbr* d_ff_nbr = nullptr;
+  double* d_ff_geo = nullptr;  // xyz0 | conv | f0, [3][nph]
+  double* d_ff_Q0 = nullptr;
+  int32_t* d_ff_flag = nullptr;  // valid [B] | pre-pass flags [ff_nchunk][B]
+  int32_t ff_chunk = 32, ff_nchunk = 1;
+  unsigned long long* d_ff_count = nullptr;
   Op op_prime;
   Chain chA[2], chB[2], chC, chNear;  // [with dyn.q]; chNear: all near-field partial tiles (priming)
   Chain chBC;                          // stages B + C fused (harmonic force, disjoint baths)
@@ -3047,12 +3060,61 @@ int prime(gle_handle* h) {
 
 int ladder_step(gle_handle* h, int early);
 
+// ---- pair force field (gle_set_pair_force) ----------------------------------------------------
+PairFFArgs ff_args(const gle_handle* h, const double* q, double* F, bool cached) {
+  PairFFArgs a{};
+  a.natom = h->ff_natom;
+  a.B = (int32_t)h->B;
+  a.cached = cached ? 1 : 0;
+  a.rp = h->d_ff_rp;
+  a.nbr = h->d_ff_nbr;
+  a.xyz0 = h->d_ff_geo;
+  a.conv = h->d_ff_geo + h->nph;
+  a.f0 = h->d_ff_geo + 2 * h->nph;
+  a.q = q;
+  a.F = F;
+  a.Q0 = h->d_ff_Q0;
+  a.valid = h->d_ff_flag;
+  a.bad = h->d_ff_flag + h->B;
+  a.chunk = h->ff_chunk;
+  a.nchunk = h->ff_nchunk;
+  a.count = h->d_ff_count;
+  return a;
+}
+
+// md.potforce(q) of the field into Fc with the cache rule per trajectory (md.py:449-450, 767-779):
+// the distance pre-pass, then the force launch, both on the main stream
+void ff_force(gle_handle* h, const double* q) {
+  const PairFFArgs a = ff_args(h, q, h->d_Fc, true);
+  launch_pair_dist(a, h->stream);
+  launch_pair_force(a, h->stream);
+}
+
+// empty the field's cache (new state, or Fc was overwritten by another force)
+int ff_forget(gle_handle* h) {
+  if (h->d_ff_flag) HIPCHK(h, hipMemsetAsync(h->d_ff_flag, 0, (size_t)h->B * sizeof(int32_t), h->stream));
+  return GLE_OK;
+}
+
+void ff_free(gle_handle* h) {
+  if (h->d_ff_rp) tfree(h->d_ff_rp);
+  if (h->d_ff_nbr) tfree(h->d_ff_nbr);
+  if (h->d_ff_geo) tfree(h->d_ff_geo);
+  h->d_ff_rp = nullptr;
+  h->d_ff_nbr = nullptr;
+  h->d_ff_geo = nullptr;
+  h->ff_set = false;
+  h->ff_natom = 0;
+  h->ff_nnbr = 0;
+}
+
 int step_begin_impl(gle_handle* h, const double* fpot_host_T) {
   if (!h->state_set) return fail(h, GLE_ERR_STATE, "gle_set_state has not been called");
   bounds_table_sync();
   for (size_t j = 0; j < h->baths.size(); ++j)
     if (!h->baths[j].noise_set) return fail(h, GLE_ERR_STATE, "bath " + std::to_string(j) + " has no noise");
-  if (fpot_host_T == nullptr && !h->has_dyn)
+  const bool use_ff = fpot_host_T == nullptr && h->ff_set;  // the pair field is the potential
+  if (fpot_host_T == nullptr && !h->has_dyn && !use_ff)
     return fail(h, GLE_ERR_STATE, "no potential force: pass fpot or call gle_set_dyn (md.py:468-470)");
   int rc = 0;
   if (h->std_stale) {
@@ -3072,12 +3134,18 @@ int step_begin_impl(gle_handle* h, const double* fpot_host_T) {
   }
   rc = ladder_step(h, 0);
   if (rc) return rc;
-  const bool need_pot = (fpot_host_T == nullptr) && !h->pot_cache_exact;
+  const bool need_pot = (fpot_host_T == nullptr) && !use_ff && !h->pot_cache_exact;
   const StepArgs ta = step_args(h);
-  if (fpot_host_T)
+  if (fpot_host_T) {
     HIPCHK(h, hipMemcpyAsync(h->d_Fc, fpot_host_T, (size_t)h->nph * h->B * 8, hipMemcpyHostToDevice, h->stream));
+    rc = ff_forget(h);  // Fc no longer holds the field's force
+    if (rc) return rc;
+  } else if (use_ff) {
+    ff_force(h, h->d_Q);  // md.potforce(q_t) into Fc: the stage runs as for a host force
+  }
   if (h->d_dbg && h->t == h->dbg_t) h->dbg_a = need_pot ? 1 : 0;  // GLE_CHAIN_DBG: the stage-A variant recorded
-  run_chain(h, 0, h->chA[need_pot ? 1 : 0], ta, (need_pot ? 1 : 0) | (fpot_host_T ? 0 : 2), h->levels.empty(), 0);
+  run_chain(h, 0, h->chA[need_pot ? 1 : 0], ta, (need_pot ? 1 : 0) | ((fpot_host_T || use_ff) ? 0 : 2),
+            h->levels.empty(), 0);
   h->host_force_step = fpot_host_T != nullptr;
   return GLE_OK;
 }
@@ -3191,8 +3259,14 @@ int ladder_step(gle_handle* h, int early) {
 int step_end_impl(gle_handle* h, const double* fpot_host_T) {
   int mode1 = 1;
   const StepArgs ta = step_args(h);
+  const bool use_ff = fpot_host_T == nullptr && h->ff_set;
   if (fpot_host_T) {
     HIPCHK(h, hipMemcpyAsync(h->d_Fc, fpot_host_T, (size_t)h->nph * h->B * 8, hipMemcpyHostToDevice, h->stream));
+    mode1 = 0;
+    const int rc = ff_forget(h);
+    if (rc) return rc;
+  } else if (use_ff) {
+    ff_force(h, h->d_Qt);  // md.potforce(q~) into Fc
     mode1 = 0;
   } else {
     if (!h->has_dyn) return fail(h, GLE_ERR_STATE, "no potential force at q~");
@@ -3232,7 +3306,7 @@ int step_end_impl(gle_handle* h, const double* fpot_host_T) {
   // the next step is a block boundary: the background blocks started there wait for this step
   if (!h->levels.empty() && (h->t + 1) % h->P0 == 0) HIPCHK(h, hipEventRecord(h->ev_step, h->stream));
   h->t += 1;
-  h->pot_cache_exact = (fpot_host_T == nullptr) && h->constr.empty();
+  h->pot_cache_exact = (fpot_host_T == nullptr) && !use_ff && h->constr.empty();
   h->std_words_live = true;  // the velocity stage wrote step t + 1's id0 distances (host force: against q~)
   HIPCHK(h, hipGetLastError());
   return GLE_OK;
@@ -3655,6 +3729,9 @@ int gle_destroy(gle_handle* h) {
     bounds_del(p);
     hipFree(p);
   }
+  for (void* p : {(void*)h->d_ff_rp, (void*)h->d_ff_nbr, (void*)h->d_ff_geo, (void*)h->d_ff_Q0, (void*)h->d_ff_flag,
+                  (void*)h->d_ff_count})
+    if (p) tfree(p);
   if (h->h_xstop) hipHostFree(h->h_xstop);
   for (auto e : h->ev) hipEventDestroy(e);
   for (auto& lv : h->levels)
@@ -3922,6 +3999,203 @@ int gle_set_constraint(gle_handle* h, const int64_t* dofs, int64_t n) {
   return GLE_OK;
 }
 
+int gle_set_pair_force(gle_handle* h, int64_t natom, const double* xyz0, const double* conv, int64_t npair,
+                       const int64_t* pair_i, const int64_t* pair_j, const int32_t* pair_type, const double* shift,
+                       int32_t ntype, const int32_t* style, const double* par) {
+  if (!h) return GLE_ERR_ARG;
+  if (npair < 0) return fail(h, GLE_ERR_ARG, "pair force: npair must be >= 0");
+  hipSetDevice(h->cfg.device);
+  XRESOLVE(h);
+  // either way the cached potential force is no longer the potential's: both caches start empty
+  auto forget = [&]() -> int {
+    int rc = ff_forget(h);
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->d_qvalid, 0, (size_t)h->B * sizeof(int32_t), h->stream));
+    if (h->d_pmax)  // (allocated with the plan)
+      HIPCHK(h, hipMemsetAsync(h->d_pmax, 0, (size_t)4 * h->B * sizeof(unsigned long long), h->stream));
+    h->pot_cache_exact = false;
+    h->std_words_live = false;
+    return GLE_OK;
+  };
+  if (npair == 0) {  // remove the field: dyn (if set) is the potential again
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    ff_free(h);
+    return forget();
+  }
+  // ---- every check on the host, before anything is uploaded (a rejected call leaves the previous field)
+  if (!xyz0 || !conv || !pair_i || !pair_j || !pair_type || !style || !par)
+    return fail(h, GLE_ERR_ARG, "pair force: null argument");
+  if (natom <= 0 || 3 * natom != h->nph)
+    return fail(h, GLE_ERR_ARG, "pair force: nph = " + std::to_string(h->nph) + " is not 3 * natom = 3 * " +
+                                    std::to_string(natom));
+  if (ntype <= 0) return fail(h, GLE_ERR_ARG, "pair force: ntype must be >= 1");
+  if (2 * npair > (int64_t)INT32_MAX) return fail(h, GLE_ERR_ARG, "pair force: too many pairs");
+  for (int64_t i = 0; i < 3 * natom; ++i)
+    if (!std::isfinite(xyz0[i]) || !std::isfinite(conv[i]))
+      return fail(h, GLE_ERR_ARG, "pair force: non-finite xyz0 / conv");
+  for (int32_t k = 0; k < ntype; ++k) {
+    const double* p = par + 4 * (size_t)k;
+    const std::string tn = "pair force: type " + std::to_string(k);
+    if (style[k] == PAIR_HARMONIC) {
+      if (!std::isfinite(p[0])) return fail(h, GLE_ERR_ARG, tn + ": non-finite k");
+      if (!std::isfinite(p[1]) || !(p[1] > 0.0)) return fail(h, GLE_ERR_ARG, tn + ": r0 must be finite and > 0");
+    } else if (style[k] == PAIR_MORSE) {
+      if (!std::isfinite(p[0])) return fail(h, GLE_ERR_ARG, tn + ": non-finite D");
+      if (!std::isfinite(p[1]) || !(p[1] > 0.0)) return fail(h, GLE_ERR_ARG, tn + ": a must be finite and > 0");
+      if (!std::isfinite(p[2]) || !(p[2] > 0.0)) return fail(h, GLE_ERR_ARG, tn + ": r0 must be finite and > 0");
+    } else if (style[k] == PAIR_LJ) {
+      if (!std::isfinite(p[0])) return fail(h, GLE_ERR_ARG, tn + ": non-finite epsilon");
+      if (!std::isfinite(p[1]) || !(p[1] > 0.0)) return fail(h, GLE_ERR_ARG, tn + ": sigma must be finite and > 0");
+    } else {
+      return fail(h, GLE_ERR_ARG, tn + ": unknown style " + std::to_string(style[k]));
+    }
+  }
+  std::vector<int32_t> rp((size_t)natom + 1, 0);
+  for (int64_t k = 0; k < npair; ++k) {
+    const std::string pn = "pair force: pair " + std::to_string(k);
+    if (pair_i[k] < 0 || pair_i[k] >= natom || pair_j[k] < 0 || pair_j[k] >= natom)
+      return fail(h, GLE_ERR_ARG, pn + ": atom index out of range");
+    if (pair_type[k] < 0 || pair_type[k] >= ntype) return fail(h, GLE_ERR_ARG, pn + ": type out of range");
+    bool zero = true;
+    if (shift)
+      for (int c = 0; c < 3; ++c) {
+        if (!std::isfinite(shift[3 * k + c])) return fail(h, GLE_ERR_ARG, pn + ": non-finite shift");
+        zero = zero && shift[3 * k + c] == 0.0;
+      }
+    if (pair_i[k] == pair_j[k] && zero) return fail(h, GLE_ERR_ARG, pn + ": i == j with zero shift");
+    rp[(size_t)pair_i[k] + 1] += 1;
+    rp[(size_t)pair_j[k] + 1] += 1;
+  }
+  for (int64_t a = 0; a < natom; ++a) rp[(size_t)a + 1] += rp[(size_t)a];
+  // neighbour table: each pair from both ends, rows in pair-list order (the summation order)
+  std::vector<PairNbr> nbr((size_t)2 * npair);
+  {
+    std::vector<int32_t> fill(rp.begin(), rp.end() - 1);
+    for (int64_t k = 0; k < npair; ++k) {
+      const double* p = par + 4 * (size_t)pair_type[k];
+      for (int end = 0; end < 2; ++end) {
+        const int64_t a = end ? pair_j[k] : pair_i[k], o = end ? pair_i[k] : pair_j[k];
+        PairNbr& n = nbr[(size_t)fill[(size_t)a]++];
+        n.j = (int32_t)o;
+        n.style = style[pair_type[k]];
+        for (int c = 0; c < 3; ++c) n.s[c] = shift ? (end ? -shift[3 * k + c] : shift[3 * k + c]) : 0.0;
+        for (int c = 0; c < 4; ++c) n.p[c] = p[c];
+      }
+    }
+  }
+  for (int64_t k = 0; k < npair; ++k) {  // no pair of coincident atoms at q = 0 (r = 0: no direction)
+    double r2 = 0.0;
+    for (int c = 0; c < 3; ++c) {
+      const double d = xyz0[3 * pair_j[k] + c] + (shift ? shift[3 * k + c] : 0.0) - xyz0[3 * pair_i[k] + c];
+      r2 += d * d;
+    }
+    if (!(r2 > 0.0))
+      return fail(h, GLE_ERR_ARG, "pair force: pair " + std::to_string(k) + ": coincident atoms at q = 0");
+  }
+  // xyz0 | conv | f0 = conv F_abs(0) (lammpsdriver.initforce; filled in by the kernel below)
+  std::vector<double> geo((size_t)9 * natom, 0.0);
+  std::copy(xyz0, xyz0 + 3 * natom, geo.begin());
+  std::copy(conv, conv + 3 * natom, geo.begin() + 3 * natom);
+  // ---- upload
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // launches of a previous field have finished
+  ff_free(h);
+  const size_t nst = (size_t)h->nph * h->B;
+  hipError_t e = hipSuccess;
+  if (!h->d_ff_Q0) {
+    // the distance pre-pass: chunks of >= 32 DOFs, at most PAIR_MAXCHUNK of them
+    h->ff_chunk = (int32_t)std::max<int64_t>(32, (h->nph + PAIR_MAXCHUNK - 1) / PAIR_MAXCHUNK);
+    h->ff_nchunk = (int32_t)((h->nph + h->ff_chunk - 1) / h->ff_chunk);
+    e = tmalloc(&h->d_ff_Q0, nst * 8);
+    if (e == hipSuccess) e = tmalloc(&h->d_ff_flag, (size_t)(1 + h->ff_nchunk) * h->B * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ff_flag, 0, (size_t)(1 + h->ff_nchunk) * h->B * sizeof(int32_t), h->stream);
+    if (e == hipSuccess) e = tmalloc(&h->d_ff_count, (size_t)h->B * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ff_Q0, 0, nst * 8, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_ff_count, 0, (size_t)h->B * sizeof(unsigned long long), h->stream);
+  }
+  if (e == hipSuccess) e = tmalloc(&h->d_ff_rp, rp.size() * sizeof(int32_t));
+  if (e == hipSuccess) e = tmalloc(&h->d_ff_nbr, nbr.size() * sizeof(PairNbr));
+  if (e == hipSuccess) e = tmalloc(&h->d_ff_geo, geo.size() * 8);
+  if (e != hipSuccess) {
+    ff_free(h);
+    for (void* p : {(void*)h->d_ff_Q0, (void*)h->d_ff_flag, (void*)h->d_ff_count})
+      if (p) tfree(p);
+    h->d_ff_Q0 = nullptr;
+    h->d_ff_flag = nullptr;
+    h->d_ff_count = nullptr;
+    return fail(h, GLE_ERR_NOMEM, std::string("pair force tables: ") + hipGetErrorString(e));
+  }
+  int rc = upload(h, h->d_ff_rp, rp.data(), rp.size() * sizeof(int32_t));
+  if (!rc) rc = upload(h, h->d_ff_nbr, nbr.data(), nbr.size() * sizeof(PairNbr));
+  if (!rc) rc = upload(h, h->d_ff_geo, geo.data(), geo.size() * 8);
+  if (!rc) rc = forget();
+  if (rc) {
+    ff_free(h);
+    return rc;
+  }
+  h->ff_natom = (int32_t)natom;
+  h->ff_nnbr = 2 * npair;
+  // f0 by the kernel itself (one column at q = 0), so that the device force at q = 0 is exactly
+  // zero, as the host drivers' force(0) = absforce(0) - f0 is
+  {
+    double* d_z = nullptr;
+    e = tmalloc(&d_z, (size_t)h->nph * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(d_z, 0, (size_t)h->nph * 8, h->stream);
+    if (e == hipSuccess) {
+      PairFFArgs a = ff_args(h, d_z, h->d_ff_geo + 2 * h->nph, false);
+      a.B = 1;
+      a.f0 = d_z;
+      launch_pair_force(a, h->stream);
+      e = hipStreamSynchronize(h->stream);
+    }
+    if (d_z) tfree(d_z);
+    if (e != hipSuccess) {
+      ff_free(h);
+      return fail(h, GLE_ERR_HIP, std::string("pair force f0: ") + hipGetErrorString(e));
+    }
+    // (finite parameters and distances can still overflow, e.g. (sigma / r)^12: no field is left set)
+    rc = download(h, geo.data(), h->d_ff_geo + 2 * h->nph, (size_t)h->nph * 8);
+    for (int64_t i = 0; !rc && i < h->nph; ++i)
+      if (!std::isfinite(geo[(size_t)i])) rc = fail(h, GLE_ERR_ARG, "pair force: non-finite force at q = 0");
+    if (rc) {
+      ff_free(h);
+      return rc;
+    }
+  }
+  h->ff_set = true;
+  return GLE_OK;
+}
+
+int gle_eval_force(gle_handle* h, const double* q, double* f) {
+  if (!h || !q || !f) return GLE_ERR_ARG;
+  if (!h->ff_set) return fail(h, GLE_ERR_STATE, "no pair force field (gle_set_pair_force)");
+  hipSetDevice(h->cfg.device);
+  const int64_t B = h->B, n = h->nph;
+  std::vector<double> tq;
+  to_dev_layout(q, tq, B, n, n);
+  double* d_tmp = nullptr;  // q | f
+  HIPCHK(h, tmalloc(&d_tmp, (size_t)2 * n * B * 8));
+  hipError_t e = hipMemcpyAsync(d_tmp, tq.data(), (size_t)n * B * 8, hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) {
+    launch_pair_force(ff_args(h, d_tmp, d_tmp + n * B, false), h->stream);  // no cache, no state change
+    e = hipMemcpyAsync(tq.data(), d_tmp + n * B, (size_t)n * B * 8, hipMemcpyDeviceToHost, h->stream);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  tfree(d_tmp);
+  if (e != hipSuccess) return fail(h, GLE_ERR_HIP, std::string("gle_eval_force: ") + hipGetErrorString(e));
+  from_dev_layout(tq, f, B, n);
+  return GLE_OK;
+}
+
+int gle_force_evals(gle_handle* h, int64_t* count) {
+  if (!h || !count) return GLE_ERR_ARG;
+  hipSetDevice(h->cfg.device);
+  if (!h->d_ff_count) {  // never had a field
+    std::fill(count, count + h->B, (int64_t)0);
+    return GLE_OK;
+  }
+  return download(h, count, h->d_ff_count, (size_t)h->B * sizeof(int64_t));
+}
+
 int gle_set_state(gle_handle* h, const double* p, const double* q, int64_t t) {
   if (!h || !p || !q) return GLE_ERR_ARG;
   if (t < 0) return fail(h, GLE_ERR_ARG, "t must be >= 0");
@@ -3941,6 +4215,8 @@ int gle_set_state(gle_handle* h, const double* p, const double* q, int64_t t) {
   h->t = t;
   HIPCHK(h, hipMemsetAsync(h->d_qvalid, 0, (size_t)B * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(h->d_pmax, 0, (size_t)B * 4 * 8, h->stream));
+  rc = ff_forget(h);
+  if (rc) return rc;
   // p_t into the history ring slot of t; q_t into the q gather
   for (auto& b : h->baths) {
     std::vector<double> col((size_t)b.nc * B), colq((size_t)b.ncp * B, 0.0);
@@ -4504,7 +4780,7 @@ int gle_run(gle_handle* h, int64_t nsteps) {
   if (!h || nsteps < 0) return GLE_ERR_ARG;
   hipSetDevice(h->cfg.device);
   XRESOLVE(h);
-  if (h->xstep && h->frozen) return run_xstep(h, nsteps);
+  if (h->xstep && h->frozen && !h->ff_set) return run_xstep(h, nsteps);  // the field is not harmonic
   for (int64_t s = 0; s < nsteps; ++s) {
     int rc = step_begin_impl(h, nullptr);
     if (rc) return rc;

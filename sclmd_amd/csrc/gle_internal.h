@@ -394,6 +394,37 @@ struct FpotArgs {
   int32_t nc[MAXBATH];
 };
 void launch_fpot(const FpotArgs& a, hipStream_t s);
+// Anharmonic pair force field (gle_set_pair_force, gle_force.hip): a static pair list held as a
+// per-atom CSR neighbour table (each pair stored from both ends, in pair-list order), one thread per
+// (atom, trajectory).  x = xyz0 + conv q, r = |x_j + shift - x_i|, F = conv F_abs(q) - f0.
+constexpr int PAIR_HARMONIC = 0, PAIR_MORSE = 1, PAIR_LJ = 2;
+constexpr int PAIR_MAXCHUNK = 32;  // DOF chunks of the cache-distance pre-pass (PairFFArgs::nchunk)
+struct PairNbr {   // 64 bytes: one neighbour of an atom
+  int32_t j;       // the other atom
+  int32_t style;   // PAIR_*
+  double s[3];     // image vector as seen from this end (shift, or -shift from the j end)
+  double p[4];     // the pair type's parameters
+};
+struct PairFFArgs {
+  int32_t natom, B;
+  int32_t cached;  // 1: md.potforce's rule (skip trajectories the pre-pass found within 1e-9 of Q0;
+                   // store Q0, valid, count)
+  int32_t chunk, nchunk;  // pre-pass: DOFs per workgroup row, rows (nchunk <= 32)
+  const int32_t* rp;    // [natom + 1]
+  const PairNbr* nbr;   // [rp[natom]]
+  const double *xyz0, *conv, *f0;  // [3 natom]
+  const double* q;      // [3 natom][B]
+  double* F;            // [3 natom][B]
+  double* Q0;           // [3 natom][B] point of the cached evaluation
+  int32_t* valid;       // [B]
+  int32_t* bad;         // [nchunk][B] written by the distance pre-pass: some DOF of the chunk is
+                        // 1e-9 or more from Q0 (or NaN)
+  unsigned long long* count;  // [B] evaluations
+};
+// pre-pass: per DOF chunk and trajectory, whether max_d |q - Q0| < 1e-9 fails (NaN: fails); a
+// trajectory hits the cache iff it is valid and no chunk fails
+void launch_pair_dist(const PairFFArgs& a, hipStream_t s);
+void launch_pair_force(const PairFFArgs& a, hipStream_t s);
 // composed one-launch step, priming one bath from the two-launch path's state at step t:
 // V0[t & 1] = n_t - c S[t & 1] (S: nullptr for a bath without memory sum), W1[t & 1] = n_{t+1} -
 // c (sum of the nqn near partials of target t+1 at parity (t + 1) & 1 + the levels at target t+1)

@@ -40,7 +40,8 @@ def ApplyConstraint(f, constr=None):
 class md:
     def __init__(self, dt, nmd, T, syslist=None, axyz=None, dyn=None, nstart=0, nstop=1, npie=1,
                  md2ang=0.06466, *, ntraj=1, seed=None, traj_offset=0, device=None,
-                 noise_mode="numpy", block_len=0, far_mode="auto", max_block=0, comm=None, verbose=True):
+                 noise_mode="numpy", block_len=0, far_mode="auto", max_block=0, comm=None, verbose=True,
+                 plan_class="auto"):
         self.nstart, self.nstop = nstart, nstop
         self.dt, self.nmd = dt, nmd
         self.T = T
@@ -48,6 +49,7 @@ class md:
         self.saveall = self.savep = self.saveq = self.rmnc = False
         self.nstep = None
         self.pforce = None
+        self._devff = None         # device-resident PairForceField (AddPotential)
         self.constraint = None
         self.atomlist = None
         self.verbose = verbose
@@ -61,6 +63,7 @@ class md:
         self.block_len = int(block_len)
         self.far_mode = far_mode
         self.max_block = int(max_block)
+        self.plan_class = plan_class  # "auto" / "small" / "large" (gle_set_plan_class): schedule only
         self.comm = comm
         self.SetXyz(axyz)
         if syslist is not None:
@@ -339,7 +342,21 @@ class md:
         ensemble.  With a list, the trajectories' driver calls of a force phase run concurrently on
         a thread pool (LAMMPS / SIESTA / DeePMD release the GIL inside their engines), so an
         ensemble's host force phase costs about one driver call instead of ntraj of them.  A single
-        driver instance is called for the trajectories one after another."""
+        driver instance is called for the trajectories one after another.
+
+        A forcefield.PairForceField with on_device=True is uploaded to the stepper instead
+        (gle_set_pair_force): it takes the place of dyn as the potential on the device, md.steps /
+        md.Run stay on the device and md.vv makes no host force call.  With on_device=False, and for
+        every other driver object, the host path is used."""
+        dev = getattr(pint, "on_device", False) and hasattr(pint, "pair_i")
+        if self._devff is not None and self._st is not None:
+            self._st.clear_pair_force()
+        self._devff = pint if dev else None
+        if dev:
+            self.pforces, self.pforce = None, None
+            if self._st is not None:
+                self._upload_devff(self._st)
+            return
         if isinstance(pint, (list, tuple)):
             if len(pint) != self.ntraj:
                 raise ValueError("AddPotential: %d drivers for %d trajectories" % (len(pint), self.ntraj))
@@ -421,6 +438,8 @@ class md:
         dev = self._device_ordinal()
         st = _native.Stepper(self.nph, self.ntraj, self.nmd, self.dt, dev, self.block_len, self.far_mode,
                              self.max_block)
+        if self.plan_class != "auto":
+            st.set_plan_class(self.plan_class)
         for b in self.baths:
             rec = getattr(b, "gmem_recipe", None)
             if rec is not None and b.__dict__.get("_kernel") is None:
@@ -437,6 +456,8 @@ class md:
                 st.add_bath(_native.GLE_BATH_PHONON, b.cids, b.kernel)
         if self.dyn is not None:
             st.set_dyn(self.dyn)
+        if self._devff is not None:
+            self._upload_devff(st)
         c = self._constr_dofs()
         if c:
             st.set_constraint(c)
@@ -446,6 +467,10 @@ class md:
             st.set_history(i, None)
         self._reset_his = False
         return st
+
+    def _upload_devff(self, st):
+        ff = self._devff
+        st.set_pair_force(ff.xyz, ff.conv, ff.pair_i, ff.pair_j, ff.types, ff.styles, ff.params, ff.shift)
 
     def _push_state(self):
         if not self._host_newer:
